@@ -9,7 +9,10 @@ sequences (embedding, 32 decoder layers through the HIP kernels, bf16 lm_head, g
 replayed from a captured hipGraph; inputs (weights, KV cache with `context` tokens per
 sequence) are resident in HBM before the timed region.
 
-Extra objects on the line:
+A plain run sets up, warms up, times exactly --steps steps and prints the line (`value`, `ms_per_step`, the step's
+HBM bound, the configuration).  `--dump-outputs DIR` also writes what the last timed step computed (dump_outputs()).
+
+Extra objects on the line, measured after the timed steps and only with `--full`:
   roofline     -- dominant kernel = the W4A16 GEMM (w4a16_stream_kernel at M <= 64): algorithmic bytes of
                   the 4 GEMMs of a layer / mean device time of those 4 launches, measured live with
                   HIP events around a hipGraph replay of the same kernels (no host launch cost).
@@ -46,8 +49,17 @@ def parse():
     ap.add_argument("--context", type=int, default=512)
     ap.add_argument("--model", default="llama3-8b")
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-sweep", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure everything beside the headline figure: `sustained`, the GEMM "
+                         "`roofline`, `ttft_ms_p50`, `batch_sweep_tokens_per_s`, `other_configs`, `cpu_baseline` (and "
+                         "`process_group_path` with NMV_BENCH_COMPARE_RCCL=1); without it the run sets up, warms up, times "
+                         "--steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed to DIR/<name>.npy (float32): "
+                         "next_tokens, kv_last_step")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave `cpu_baseline` out")
+    ap.add_argument("--no-sweep", action="store_true",
+                    help="with --full: leave out `sustained`, `ttft_ms_p50`, the batch sweep and `other_configs`")
     ap.add_argument("--e2e", action="store_true",
                     help="add `e2e`: prompt 512 -> 128 greedy tokens for batch 1..64, 3 + 10 runs (SURVEY 8d); ~1 min more")
     ap.add_argument("--kv-cache-dtype", default="auto")
@@ -420,6 +432,31 @@ def cpu_baseline(arch, batch, context, budget_s=12.0):
                               "note": "oracle.c's clarity-first dequant+GEMM (the parity checker), one call"}}
 
 
+DUMP_KV_BYTES = 32 << 20   # budget of kv_last_step.npy (the two files together stay far below 64 MB)
+
+
+@torch.inference_mode()
+def dump_outputs(runner, tokens, path):
+    """--dump-outputs: what the last timed step handed its caller, as float32 .npy files under `path`.
+    next_tokens  [batch]: the return value of decode_step(), the greedy token of every sequence (ids are exact in
+                 float32: the vocabulary is far below 2^24).
+    kv_last_step [layers, 2, n_seq, block_size * kv_heads * head_dim]: the caller's KV-cache blocks into which that
+                 step wrote its token's K / V (fp8 caches: the raw codes as numbers), for the first n_seq sequences
+                 of the batch -- as many as fit DUMP_KV_BYTES, a fixed choice, so two builds dump the same blocks.
+    Weights, block tables, first tokens and the KV context all come from fixed seeds: the same arguments give the
+    same inputs in every run."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "next_tokens.npy"), tokens.detach().cpu().numpy().astype(np.float32))
+    bs = runner.cache_config.block_size
+    pos = runner.positions - 1      # every step advances the positions on the device: where the last one wrote
+    blk = torch.gather(runner.block_tables.long(), 1, (pos // bs).view(-1, 1)).view(-1)
+    per_seq = len(runner.kv_caches) * 2 * runner.kv_caches[0].shape[2] * 4
+    n_seq = max(1, min(runner.batch, DUMP_KV_BYTES // per_seq))
+    kv = torch.stack([c[:, blk[:n_seq]].float() for c in runner.kv_caches])
+    np.save(os.path.join(path, "kv_last_step.npy"), kv.cpu().numpy())
+
+
 EXIT_CAPTURE_FAILED = 75   # EX_TEMPFAIL: the ranks ask to be restarted with --no-graph
 
 
@@ -554,7 +591,7 @@ def main():
         ctx0 = int(runner.seq_lens[0])       # tokens the first timed step attends to (the new one included)
         t0 = time.perf_counter()
         for _ in range(steps):
-            runner.decode_step()
+            last_tokens[0] = runner.decode_step()
         torch.cuda.synchronize(dev)
         if world > 1:
             nd.get_tp_group().barrier()
@@ -565,7 +602,12 @@ def main():
         return dt, graphed
 
     timed_ctx = [args.context, args.context]   # context of the first / last step of the last measure() call
+    last_tokens = [None]                       # what its last timed step returned
     dt, graphed = measure(args.batch, args.steps, args.warmup)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(runner, last_tokens[0], args.dump_outputs)
+    # a plain run stops at the headline figure; --full adds the measurements that take runs of their own
+    sweeps = args.full and not args.no_sweep
     ctx_first, ctx_last = timed_ctx
     ms_per_step = dt / args.steps * 1e3
     value = args.batch * args.steps / dt
@@ -589,7 +631,7 @@ def main():
                    "context_len_timed_steps": [ctx_first, ctx_last],
                    "parallelism": f"tp{world}", "hip_graph": graphed},
     }
-    if dt < 0.5 and not args.no_sweep:
+    if dt < 0.5 and sweeps:
         # the contract times exactly --steps steps; when that region is short, a longer one is measured
         # as well and reported beside it (it never replaces `value`)
         long_steps = 256
@@ -625,7 +667,7 @@ def main():
             msg = args.batch * arch.hidden_size * 2
             out["config"]["all_reduce"] = (f"p2p {'two-shot' if car.is_two_shot(msg) else 'one-shot'} over HIP IPC, "
                                            f"fused with residual-add + RMSNorm ({msg} B per call)")
-            if os.environ.get("NMV_BENCH_COMPARE_RCCL", "0") == "1" and not args.no_sweep:
+            if os.environ.get("NMV_BENCH_COMPARE_RCCL", "0") == "1" and sweeps:
                 # opt-in (NMV_BENCH_COMPARE_RCCL=1): the same step with the P2P communicator switched off -- every
                 # all-reduce / gather through the process group (RCCL) -- so that the scaling curve can be read for
                 # both.  Not by default: a fault in that second path would cost the line of the first.
@@ -647,23 +689,23 @@ def main():
         out["step_roofline"] = {"weight_bytes": wb, "kv_bytes": kvb, "mean_context": mean_ctx,
                                 "hbm_bound_ms": round((wb + kvb) / (HBM_PEAK_GBS * 1e9) * 1e3, 4),
                                 "frac_of_hbm_bound": round((wb + kvb) / (HBM_PEAK_GBS * 1e9) / (ms_per_step * 1e-3), 4)}
-        if args.quant == "w4a16":
+        if args.full and args.quant == "w4a16":
             out["roofline"] = gemm_roofline(runner, args.batch, dev)
-    if rank == 0 and world == 1 and not args.no_sweep:
+    if rank == 0 and world == 1 and sweeps:
         out["ttft_ms_p50"] = {"prompt_tokens": args.context, "batch": 1,
                               "value": ttft(runner, dev, args.context)}
         if args.quant == "w4a16":
             out["ttft_ms_p50"]["gemm_roofline"] = prefill_gemm_roofline(runner, args.context, dev)
     if rank == 0 and world == 1 and args.e2e:
         out["e2e"] = e2e_latency(runner, dev, prompt_len=args.context)
-    if world == 1 and not args.no_sweep:
+    if world == 1 and sweeps:
         sweep = {}
         for b in (1, 8, 32):
             d, _ = measure(b, max(16, args.steps // 2), 4)
             sweep[str(b)] = round(b * max(16, args.steps // 2) / d, 1)
         sweep[str(args.batch)] = round(value, 1)
         out["batch_sweep_tokens_per_s"] = sweep
-    if rank == 0 and world == 1 and not args.no_sweep and args.quant == "w4a16" and args.model == "llama3-8b":
+    if rank == 0 and world == 1 and sweeps and args.quant == "w4a16" and args.model == "llama3-8b":
         # BASELINE.json's other single-GPU configurations, in the same driver-visible line: config 3 (w8a8 + fp8 KV) and
         # config 1 (bf16), batch args.batch, 64 timed steps each; skipped when the run is already long
         others = {}
@@ -682,7 +724,7 @@ def main():
             except Exception as e:   # never take the headline number down
                 others[tag] = {"value": None, "error": repr(e)}
         out["other_configs"] = others
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         try:
             out["cpu_baseline"] = cpu_baseline(arch, args.batch, args.context)
         except Exception as e:  # the baseline must never take the GPU number down with it

@@ -33,7 +33,7 @@ def test_world_size_mismatch_is_refused_without_a_json_line():
 def test_help_lists_the_contract_flags():
     res = _run(["--help"], {})
     assert res.returncode == 0
-    for flag in ("--gpus", "--steps", "--warmup"):
+    for flag in ("--gpus", "--steps", "--warmup", "--full", "--dump-outputs"):
         assert flag in res.stdout
 
 

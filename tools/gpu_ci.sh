@@ -25,7 +25,7 @@ for step in "$@"; do
     lm)     run t_lm python -m pytest tests/test_gpu_linear_methods.py -q -m gpu --timeout 300 ;;
     w4)     run t_w4 python -m pytest tests/test_gpu_w4a16.py -q -m gpu --timeout 300 ;;
     all)    run t_all python -m pytest tests -q -m gpu --timeout 300 ;;
-    bench)  run bench python bench.py ;;
+    bench)  run bench python bench.py --full ;;
     gemm)   run gemm python tools/bench_gemm.py ;;
     gemmprof) cd /tmp && export TMPDIR=/tmp && cd - >/dev/null
             run gemmprof rocprofv3 --kernel-trace --output-format csv -d gpurun_out/gprof -- python tools/bench_gemm.py ${GEMM_ARGS:-}
