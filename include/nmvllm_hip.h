@@ -392,6 +392,20 @@ int nmv_prefix_prefill_attention(void* out, const void* q, const void* key_cache
                                  int64_t o_stride, int64_t kv_block_stride, int64_t kv_head_stride,
                                  const float* alibi_slopes, int sliding_window, nmv_dtype_t dtype,
                                  void* stream);
+/* The same on an fp8 KV cache (csrc/prefix_attention_fp8.hip; not in the reference, whose forward_prefix takes no
+ * cache dtype): key_cache [NB, KVH, D/16, BS, 16] and value_cache [NB, KVH, D, BS] hold e4m3 bytes, so the two
+ * cache strides are in bytes; kv_dtype must be NMV_KV_FP8_E4M3; a cached byte b stands for e4m3(b) * kv_scale, as
+ * for paged_attention.  fp16 / bf16 queries, head size 64 / 128, block size 8 / 16 / 32.  Every key and value is
+ * read from the cache, the new tokens' included: a chunk attends to the quantised values of its own tokens. */
+int nmv_prefix_prefill_attention_fp8(void* out, const void* q, const void* key_cache,
+                                     const void* value_cache, const int32_t* block_tables,
+                                     const int32_t* query_start_loc, const int32_t* seq_lens,
+                                     const int32_t* context_lens, int num_seqs, int max_query_len,
+                                     int max_blocks_per_seq, int block_size, int num_heads,
+                                     int num_kv_heads, int head_size, float scale, int64_t q_stride,
+                                     int64_t o_stride, int64_t kv_block_stride, int64_t kv_head_stride,
+                                     const float* alibi_slopes, int sliding_window, nmv_dtype_t dtype,
+                                     nmv_kv_dtype_t kv_dtype, float kv_scale, void* stream);
 int nmv_prefill_attention(void* out, const void* q, const void* k, const void* v,
                           const int32_t* cu_seqlens, int num_seqs, int max_seq_len, int num_heads,
                           int num_kv_heads, int head_size, float scale, int64_t q_stride,

@@ -325,10 +325,13 @@ def prefix_prefill_attention(out: torch.Tensor, query: torch.Tensor, key_cache: 
                              query_start_loc: torch.Tensor, seq_lens: torch.Tensor,
                              context_lens: torch.Tensor, max_query_len: int, scale: float,
                              alibi_slopes: Optional[torch.Tensor] = None,
-                             sliding_window: Optional[int] = None) -> None:
+                             sliding_window: Optional[int] = None, kv_cache_dtype: str = "auto",
+                             kv_scale: float = 1.0) -> None:
+    """kv_cache_dtype "fp8" / "fp8_e4m3": uint8 caches, key_cache [NB, KVH, D/16, BS, 16]"""
     from neural_magic_vllm_amd import _torch_bindings as tb
     tb.prefix_prefill_attention(out, query, key_cache, value_cache, block_tables, query_start_loc,
-                                seq_lens, context_lens, max_query_len, scale, alibi_slopes, sliding_window)
+                                seq_lens, context_lens, max_query_len, scale, alibi_slopes, sliding_window,
+                                kv_cache_dtype, kv_scale)
 
 
 # AWQ / asymmetric checkpoints on the Marlin kernel (not ops of nm-vllm 0.5.1; later vLLM: awq_marlin)

@@ -464,19 +464,40 @@ def prefill_attention(out, query, key, value, cu_seqlens, max_seq_len, scale, al
 
 def prefix_prefill_attention(out, query, key_cache, value_cache, block_tables, query_start_loc,
                              seq_lens, context_lens, max_query_len, scale, alibi_slopes=None,
-                             sliding_window=None) -> None:
-    """PagedAttention.forward_prefix on the paged cache (csrc/prefill_attention.hip); query/out
-    [new tokens, H, D]; key_cache [NB, KVH, D/x, BS, x], value_cache [NB, KVH, D, BS] (16-bit)"""
+                             sliding_window=None, kv_cache_dtype="auto", kv_scale=1.0) -> None:
+    """PagedAttention.forward_prefix on the paged cache; query/out [new tokens, H, D]; key_cache
+    [NB, KVH, D/x, BS, x], value_cache [NB, KVH, D, BS].  kv_cache_dtype "auto": 16-bit caches in the model
+    dtype, x = 8 (csrc/prefill_attention.hip).  "fp8" / "fp8_e4m3": uint8 caches of e4m3 bytes, x = 16, a byte
+    standing for e4m3(b) * kv_scale (csrc/prefix_attention_fp8.hip).  Either way every key and value comes from
+    the cache, the new tokens' included (the backend has written them): with an fp8 cache a chunk attends to
+    the quantised values of its own tokens, the values every later decode step sees."""
     _req(query.dim() == 3 and out.dim() == 3 and query.stride(2) == 1 and out.stride(2) == 1,
          "prefix_prefill_attention: [T, H, D] tensors with a contiguous head dim")
     t, h, d = query.shape
     _req(query.stride(1) == d and out.stride(1) == d, "prefix_prefill_attention: heads must be packed")
+    for x in (block_tables, query_start_loc, seq_lens, context_lens):
+        _req(x.dtype == torch.int32 and x.is_contiguous(), "prefix_prefill_attention: int32 index tensors")
+    if kv_cache_dtype != "auto":
+        kv_code = kv_dtype_code(kv_cache_dtype)   # raises for anything but fp8 / fp8_e4m3
+        _req(key_cache.dtype == torch.uint8 and value_cache.dtype == torch.uint8,
+             "prefix_prefill_attention: an fp8 kv cache is passed as uint8 tensors")
+        _req(value_cache.dim() == 4 and value_cache.shape[2] == d and value_cache.is_contiguous(),
+             "prefix_prefill_attention: fp8 value_cache [NB, KVH, D, BS], contiguous")
+        nb, kvh, _, bs = value_cache.shape
+        _req(d % 16 == 0 and key_cache.shape == (nb, kvh, d // 16, bs, 16) and key_cache.is_contiguous(),
+             "prefix_prefill_attention: fp8 key_cache [NB, KVH, D/16, BS, 16], contiguous")
+        with device_guard(query):
+            check(_lib.load().nmv_prefix_prefill_attention_fp8(
+                ptr(out), ptr(query), ptr(key_cache), ptr(value_cache), ptr(block_tables),
+                ptr(query_start_loc), ptr(seq_lens), ptr(context_lens), seq_lens.numel(),
+                int(max_query_len), block_tables.shape[1], bs, h, kvh, d, float(scale), query.stride(0),
+                out.stride(0), value_cache.stride(0), value_cache.stride(1), _alibi_arg(alibi_slopes, h, query),
+                int(sliding_window or 0), dtype_code(query.dtype), kv_code, float(kv_scale), stream_of(query)))
+        return
     _req(key_cache.dtype == query.dtype and value_cache.dtype == query.dtype,
          "prefix_prefill_attention: kv cache dtype must be auto (the model dtype), as for the reference's "
          "forward_prefix (vllm/attention/ops/paged_attn.py:184-216 passes no cache dtype)")
     nb, kvh, _, bs = value_cache.shape
-    for x in (block_tables, query_start_loc, seq_lens, context_lens):
-        _req(x.dtype == torch.int32 and x.is_contiguous(), "prefix_prefill_attention: int32 index tensors")
     with device_guard(query):
         check(_lib.load().nmv_prefix_prefill_attention(
             ptr(out), ptr(query), ptr(key_cache), ptr(value_cache), ptr(block_tables),

@@ -7,6 +7,9 @@ reshape_and_cache -> prefill attention -> PagedAttention.forward_decode (:441).
 Prefill runs the reference's "naive" option (torch SDPA per sequence, :379-403 / :459-491):
 the reference's default there is a Triton kernel, which this build does not ship; a gfx950
 flash-prefill kernel is row (f)-2 of SURVEY.md section 8 (next).
+Prefix-enabled prefill (chunked prefill / prefix caching, PagedAttention.forward_prefix) accepts
+kv_cache_dtype "fp8" as well as "auto": the chunk then attends to the quantised values of its own
+tokens, which the cache write above has just stored (csrc/prefix_attention_fp8.hip).
 """
 from dataclasses import dataclass
 from typing import Any, Dict, List, Optional, Tuple, Type
@@ -237,13 +240,13 @@ class ROCmHipAttentionImpl(AttentionImpl):
                     and pm.block_tables is not None and pm.block_tables.numel() > 0 \
                     and bool((pm.context_lens_tensor > 0).any()):
                 # prefix-enabled prefill (chunked prefill / prefix caching): every key comes from
-                # the paged cache, which already holds the new tokens (written above)
-                if self.kv_cache_dtype != "auto":
-                    raise NotImplementedError("prefix-enabled prefill needs kv_cache_dtype auto")
+                # the paged cache, which already holds the new tokens (written above) -- with an fp8 cache, their
+                # quantised values
                 output[:num_prefill_tokens] = PagedAttention.forward_prefix(
                     query[:num_prefill_tokens], key[:num_prefill_tokens], value[:num_prefill_tokens],
                     key_cache, value_cache, pm.block_tables, pm.query_start_loc, pm.seq_lens_tensor,
-                    pm.context_lens_tensor, pm.max_query_len, self.alibi_slopes, self.sliding_window, self.scale)
+                    pm.context_lens_tensor, pm.max_query_len, self.alibi_slopes, self.sliding_window, self.scale,
+                    self.kv_cache_dtype, kv_scale)
             elif ops.prefill_attention_supported(self.head_size) and query.dtype in (torch.float16, torch.bfloat16):
                 # the hand-written HIP flash-attention forward (csrc/prefill_attention.hip)
                 cu = pm.seq_start_loc

@@ -148,12 +148,16 @@ class PagedAttention:
                        value_cache: torch.Tensor, block_tables: torch.Tensor, query_start_loc: torch.Tensor,
                        seq_lens_tensor: torch.Tensor, context_lens: torch.Tensor, max_query_len: int,
                        alibi_slopes: Optional[torch.Tensor], sliding_window: Optional[int],
-                       scale: Optional[float] = None) -> torch.Tensor:
+                       scale: Optional[float] = None, kv_cache_dtype: str = "auto",
+                       kv_scale: float = 1.0) -> torch.Tensor:
         """new tokens attending to their whole sequence in the paged cache (paged_attn.py:184-216).  `key` / `value`
         are taken for signature parity only: the backend has written them to the cache already, and the kernel
-        reads every key from there (cache dtype auto, as the reference's forward_prefix)."""
+        reads every key from there.  The reference's forward_prefix takes no cache dtype; here kv_cache_dtype
+        "fp8" / "fp8_e4m3" reads a uint8 cache scaled by kv_scale, so a chunk attends to the quantised values of its
+        own tokens -- the values every later decode step sees."""
         as_i32 = [t.to(torch.int32) for t in (query_start_loc, seq_lens_tensor, context_lens)]
         out = torch.empty_like(query)
         ops.prefix_prefill_attention(out, query, key_cache, value_cache, block_tables, *as_i32, max_query_len,
-                                     query.shape[-1]**-0.5 if scale is None else scale, alibi_slopes, sliding_window)
+                                     query.shape[-1]**-0.5 if scale is None else scale, alibi_slopes, sliding_window,
+                                     kv_cache_dtype, kv_scale)
         return out

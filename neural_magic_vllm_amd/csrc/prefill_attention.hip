@@ -20,24 +20,9 @@
 //                              just a permutation of the contraction index); V^T comes from an LDS
 //                              copy of the 64-key V tile read with that same key order.
 // The rescale factor alpha, the running max and the row sum live per lane (its query row).
-#include "common.h"
+#include "fa_common.h"
 
 namespace nmv {
-
-constexpr int FA_QT = 64;   // queries per workgroup
-constexpr int FA_KT = 64;   // keys per iteration
-
-template <typename T> struct FaMfma;
-template <> struct FaMfma<BF16> {
-  static __device__ __forceinline__ f32x4_t run(uint4 a, uint4 b, f32x4_t c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
-  }
-};
-template <> struct FaMfma<F16> {
-  static __device__ __forceinline__ f32x4_t run(uint4 a, uint4 b, f32x4_t c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
-  }
-};
 
 typedef short v4s_t __attribute__((ext_vector_type(4)));
 typedef v4s_t __attribute__((address_space(3))) lds_v4s_t;
@@ -54,16 +39,6 @@ struct FaParams {
   const float* alibi_slopes;  // [H] or null: bias slope * (key - query) on the scaled logits
   int window;                 // sliding window (0 = none): a query sees the keys less than `window` positions back
 };
-
-// logit of (query position qp, key position key) after the softmax scale: ALiBi bias, causal / length mask
-// (-inf) and the sliding window, which the reference masks with -10000 rather than -inf because a whole tile of
-// a row may lie outside the window (prefix_prefill.py:130-144, :201-204; alibi :552-557)
-__device__ __forceinline__ float fa_mask(float x, int key, int qp, int L, float slope, int window) {
-  x += slope * (float)(key - qp);
-  if (window > 0 && qp - key >= window) x = -10000.f;
-  if (key > qp || key >= L) x = -INFINITY;
-  return x;
-}
 
 // QU = 16-query sub-tiles per wave: 1 (64 queries per workgroup; short prompts, more workgroups) or
 // 2 (128 queries: every K / V operand read from LDS feeds two MFMAs).
