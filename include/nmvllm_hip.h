@@ -373,7 +373,10 @@ int nmv_awq_dequantize(void* out, const int32_t* qweight, const void* scales, co
  *  dispatches to Triton / CK flash-attention or torch SDPA; no C++ symbol exists there.)
  * q [tokens, H, D], k / v [tokens, KVH, D], out [tokens, H, D]: token strides in elements (q, k, v
  * may be slices of the fused qkv GEMM output); cu_seqlens int32 [num_seqs + 1] on the device.
+ * Head sizes 64, 96, 112, 128, 192 and 256, fp16 / bf16, for nmv_prefill_attention and for
+ * nmv_prefix_prefill_attention (16-bit cache); any other head size is refused by both.
  * ---------------------------------------------------------------------------------------- */
+/* 1 for the head sizes listed above, else 0 (80 included) */
 int nmv_prefill_attention_supported(int head_size);
 /* Prefix-enabled prefill (PagedAttention.forward_prefix, vllm/attention/ops/paged_attn.py:184-216 ->
  * Triton context_attention_fwd): the new tokens [query_start_loc[i], query_start_loc[i+1]) of sequence
@@ -395,7 +398,8 @@ int nmv_prefix_prefill_attention(void* out, const void* q, const void* key_cache
 /* The same on an fp8 KV cache (csrc/prefix_attention_fp8.hip; not in the reference, whose forward_prefix takes no
  * cache dtype): key_cache [NB, KVH, D/16, BS, 16] and value_cache [NB, KVH, D, BS] hold e4m3 bytes, so the two
  * cache strides are in bytes; kv_dtype must be NMV_KV_FP8_E4M3; a cached byte b stands for e4m3(b) * kv_scale, as
- * for paged_attention.  fp16 / bf16 queries, head size 64 / 128, block size 8 / 16 / 32.  Every key and value is
+ * for paged_attention.  fp16 / bf16 queries, head size 64 / 128 only (the fp8 path has not followed the 16-bit one
+ * to 96 / 112 / 192 / 256), block size 8 / 16 / 32.  Every key and value is
  * read from the cache, the new tokens' included: a chunk attends to the quantised values of its own tokens. */
 int nmv_prefix_prefill_attention_fp8(void* out, const void* q, const void* key_cache,
                                      const void* value_cache, const int32_t* block_tables,

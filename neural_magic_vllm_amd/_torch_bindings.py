@@ -443,7 +443,8 @@ def prefill_attention(out, query, key, value, cu_seqlens, max_seq_len, scale, al
                       sliding_window=None) -> None:
     """varlen causal GQA prompt attention (csrc/prefill_attention.hip); q [T, H, D], k/v [T, KVH, D]
     (last dim contiguous, may be slices of qkv), cu_seqlens int32 [num_seqs + 1]; optional ALiBi slopes
-    (float32 [H]) and sliding window (keys fewer than that many positions back)"""
+    (float32 [H]) and sliding window (keys fewer than that many positions back).  Head sizes 64, 96, 112, 128, 192
+    and 256 (prefill_attention_supported); anything else raises NmvError"""
     _req(query.dim() == 3 and key.dim() == 3 and value.dim() == 3 and out.dim() == 3, "prefill_attention: [T, H, D] tensors")
     _req(query.stride(2) == 1 and key.stride(2) == 1 and value.stride(2) == 1 and out.stride(2) == 1,
          "prefill_attention: head dim must be contiguous")
@@ -467,8 +468,9 @@ def prefix_prefill_attention(out, query, key_cache, value_cache, block_tables, q
                              sliding_window=None, kv_cache_dtype="auto", kv_scale=1.0) -> None:
     """PagedAttention.forward_prefix on the paged cache; query/out [new tokens, H, D]; key_cache
     [NB, KVH, D/x, BS, x], value_cache [NB, KVH, D, BS].  kv_cache_dtype "auto": 16-bit caches in the model
-    dtype, x = 8 (csrc/prefill_attention.hip).  "fp8" / "fp8_e4m3": uint8 caches of e4m3 bytes, x = 16, a byte
-    standing for e4m3(b) * kv_scale (csrc/prefix_attention_fp8.hip).  Either way every key and value comes from
+    dtype, x = 8, head sizes 64 / 128 (csrc/prefill_attention.hip) and 96 / 112 / 192 / 256
+    (csrc/prefix_attention_staged.hip).  "fp8" / "fp8_e4m3": uint8 caches of e4m3 bytes, x = 16, a byte
+    standing for e4m3(b) * kv_scale, head sizes 64 / 128 (csrc/prefix_attention_fp8.hip).  Either way every key and value comes from
     the cache, the new tokens' included (the backend has written them): with an fp8 cache a chunk attends to
     the quantised values of its own tokens, the values every later decode step sees."""
     _req(query.dim() == 3 and out.dim() == 3 and query.stride(2) == 1 and out.stride(2) == 1,
@@ -508,6 +510,7 @@ def prefix_prefill_attention(out, query, key_cache, value_cache, block_tables, q
 
 
 def prefill_attention_supported(head_size: int) -> bool:
+    """True for the head sizes the prompt kernels are built for: 64, 96, 112, 128, 192 and 256"""
     return bool(_lib.load().nmv_prefill_attention_supported(int(head_size)))
 
 

@@ -259,8 +259,9 @@ class ROCmHipAttentionImpl(AttentionImpl):
                                       self.sliding_window)
             else:
                 if self.sliding_window is not None:
-                    raise NotImplementedError("sliding-window prompts need head size 64 or 128")
-                # head sizes other than 64 / 128: the reference's "naive" SDPA option
+                    raise NotImplementedError("sliding-window prompts need a head size the prompt kernel is built "
+                                              "for (64, 96, 112, 128, 192, 256) and fp16 / bf16")
+                # head size 80 and fp32: the reference's "naive" SDPA option
                 output[:num_prefill_tokens] = _sdpa_prefill(query[:num_prefill_tokens],
                                                             key[:num_prefill_tokens],
                                                             value[:num_prefill_tokens], pm.seq_lens,

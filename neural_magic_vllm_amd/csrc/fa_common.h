@@ -1,22 +1,34 @@
-// What the prompt-attention kernels share (prefill_attention.hip, prefix_attention_fp8.hip): the tile sizes,
-// the MFMA of the model dtype and the logit mask.
+// What the prompt-attention kernels share (prefill_attention.hip, prefix_attention_staged.hip,
+// prefix_attention_fp8.hip): the tile sizes, the MFMAs of the model dtype, the logit mask and the parameters of
+// the 16-bit prefix kernels.
 #pragma once
 #include "common.h"
 
 namespace nmv {
 
 constexpr int FA_QT = 64;   // queries per workgroup
-constexpr int FA_KT = 64;   // keys per iteration
+constexpr int FA_KT = 64;   // keys per iteration (head sizes up to 128; the wider ones choose their own, see the kernels)
+
+typedef short s16x4_t __attribute__((ext_vector_type(4)));
+typedef _Float16 f16x4_t __attribute__((ext_vector_type(4)));
 
 template <typename T> struct FaMfma;
 template <> struct FaMfma<BF16> {
   static __device__ __forceinline__ f32x4_t run(uint4 a, uint4 b, f32x4_t c) {
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
   }
+  // the 16-wide tail of a contraction whose length is 16 mod 32 (head size 112): v_mfma_f32_16x16x16.  Lane
+  // (r, g) supplies k = 4g .. 4g+3 of row / column r; the accumulator layout is that of the 32-wide step
+  static __device__ __forceinline__ f32x4_t run16(uint2 a, uint2 b, f32x4_t c) {
+    return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(__builtin_bit_cast(s16x4_t, a), __builtin_bit_cast(s16x4_t, b), c, 0, 0, 0);
+  }
 };
 template <> struct FaMfma<F16> {
   static __device__ __forceinline__ f32x4_t run(uint4 a, uint4 b, f32x4_t c) {
     return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
+  }
+  static __device__ __forceinline__ f32x4_t run16(uint2 a, uint2 b, f32x4_t c) {
+    return __builtin_amdgcn_mfma_f32_16x16x16f16(__builtin_bit_cast(f16x4_t, a), __builtin_bit_cast(f16x4_t, b), c, 0, 0, 0);
   }
 };
 
@@ -29,5 +41,26 @@ __device__ __forceinline__ float fa_mask(float x, int key, int qp, int L, float 
   if (key > qp || key >= L) x = -INFINITY;
   return x;
 }
+
+// prefix-enabled prefill on a 16-bit cache: prefix_attention_kernel (prefill_attention.hip, head sizes 64 / 128)
+// and prefix_attention_staged_kernel (prefix_attention_staged.hip, head sizes 96 / 112 / 192 / 256)
+struct PfxParams {
+  const uint16_t* q;    // [new tokens, H, D]
+  uint16_t* out;
+  const uint16_t* kc;   // key cache
+  const uint16_t* vc;   // value cache
+  const int* block_tables;   // [num_seqs, max_blocks]
+  const int* q_start;        // [num_seqs + 1] offsets of the new tokens
+  const int* seq_lens;       // [num_seqs] context + new
+  const int* ctx_lens;       // [num_seqs]
+  int64_t q_stride, o_stride, kv_block_stride, kv_head_stride;  // elements
+  int max_blocks, block_size, num_heads, num_kv_heads;
+  float scale;
+  const float* alibi_slopes;  // [H] or null
+  int window;                 // sliding window, 0 = none
+};
+
+// launches prefix_attention_staged_kernel; false when (head_size, p.block_size) has no instantiation
+bool launch_prefix_staged(const PfxParams& p, bool bf16, int head_size, dim3 grid, hipStream_t s);
 
 }  // namespace nmv

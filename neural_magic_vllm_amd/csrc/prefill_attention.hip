@@ -40,22 +40,45 @@ struct FaParams {
   int window;                 // sliding window (0 = none): a query sees the keys less than `window` positions back
 };
 
+// The tile plan per head size.  A K + V image pair of KT keys is 2 * KT * (D + 8) * 2 bytes.  A gfx950 CU has
+// 160 KiB of LDS and the compiler accepts more than 64 KiB of it per workgroup (head size 128 has always used
+// 69632 B), so the plan is a choice, not a limit: keep two workgroups on a CU.
+//   D <= 128  64 keys per iteration, double buffered (D = 112: 61440 B, D = 128: 69632 B)
+//   D  = 192  32 keys, double buffered (51200 B; 64 keys would be 102400 B: one workgroup per CU)
+//   D  = 256  32 keys, ONE buffer (33792 B): the next tile still waits in registers while this one is consumed, and
+//             is parked between two barriers, as prefix_attention_fp8_kernel does.  Two buffers (67584 B) were
+//             measured against it: DESIGN.md 3.8
+template <int D> struct FaPlan {
+  static constexpr int KT = D <= 128 ? FA_KT : 32;                          // keys per iteration
+  static constexpr bool DB = D != 256;                                      // double buffered
+  // waves per SIMD asked of the register allocator: the highest that leaves no scratch and that the LDS image
+  // lets run; 64 and 128 keep the allocator's default
+  static constexpr int WAVES = D == 64 || D == 128 ? 1 : (D == 96 || D == 192 ? 3 : 2);
+};
+
 // QU = 16-query sub-tiles per wave: 1 (64 queries per workgroup; short prompts, more workgroups) or
 // 2 (128 queries: every K / V operand read from LDS feeds two MFMAs).
 template <typename T, int D, int QU>
-__global__ __launch_bounds__(256) void prefill_attention_kernel(const FaParams p) {
+__global__ __launch_bounds__(256, FaPlan<D>::WAVES) void prefill_attention_kernel(const FaParams p) {
   constexpr int QT = FA_QT * QU;      // queries per workgroup
-  static_assert(D % 32 == 0 && D <= 256, "head size");
-  constexpr int DC = D / 32;          // 32-wide head-dim chunks (MFMA k-steps of Q.K^T)
+  static_assert(D % 16 == 0 && D <= 256, "head size");
+  constexpr int KT = FaPlan<D>::KT;   // keys per iteration
+  constexpr bool DB = FaPlan<D>::DB;
+  constexpr int NT = KT / 16;         // 16-key tiles of S
+  constexpr int NS = KT / 32;         // 32-key steps of P.V
+  constexpr int DC = D / 32;          // whole 32-wide head-dim chunks (MFMA k-steps of Q.K^T)
+  constexpr bool TAIL = D % 32 != 0;  // and a 16-wide tail (head size 112): one v_mfma_f32_16x16x16
   constexpr int DT = D / 16;          // 16-wide head-dim tiles of the output
   constexpr int VS = D + 8;           // LDS row stride of a K / V tile (elements): odd multiple of 16 B
                                       // -> conflict-free ds_read_b128 rows and transposed reads
-  constexpr int TILE = FA_KT * VS;    // elements of one tile image
-  constexpr int PIECES = FA_KT * D / 8;             // 16-byte pieces of a tile
+  static_assert((VS / 8) % 2 == 1, "row stride must be an odd multiple of 16 bytes");
+  constexpr int TILE = KT * VS;       // elements of one tile image
+  constexpr int PIECES = KT * D / 8;                // 16-byte pieces of a tile
   constexpr int PPT = (PIECES + 255) / 256;         // pieces per thread
-  static_assert(PIECES % 256 == 0, "whole pieces per thread");
-  // K and V tiles, double buffered: tile kt+1 is fetched into registers while tile kt is consumed
-  __shared__ __attribute__((aligned(16))) uint16_t kv_s[2 * 2 * TILE];
+  constexpr bool RAGGED = PIECES % 256 != 0;        // the last round is not whole (D = 112: 3.5 pieces per thread)
+  // K and V tiles: tile kt+1 is fetched into registers while tile kt is consumed, and parked in the other buffer
+  // (DB) or, after a barrier, in the same one
+  __shared__ __attribute__((aligned(16))) uint16_t kv_s[(DB ? 2 : 1) * 2 * TILE];
 
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -73,11 +96,13 @@ __global__ __launch_bounds__(256) void prefill_attention_kernel(const FaParams p
 
   // ---- Q fragments of the wave (B operand of S^T = K . Q^T): 8 head dims per lane and chunk ----
   uint4 qf[QU][DC];
+  uint2 qtail[QU];                                 // TAIL: dims D - 16 + 4 g .. + 3
 #pragma unroll
   for (int u = 0; u < QU; ++u) {
     const uint16_t* qp = p.q + (int64_t)(tok0 + min(q_row[u], L - 1)) * p.q_stride + (int64_t)head * D + g * 8;
 #pragma unroll
     for (int c = 0; c < DC; ++c) qf[u][c] = ld16(qp + c * 32);
+    if constexpr (TAIL) qtail[u] = ld8(qp - g * 4 + DC * 32);
   }
   f32x4_t o[QU][DT];
   float m_run[QU], l_run[QU];             // per lane = per query row (l: this lane's share)
@@ -92,9 +117,9 @@ __global__ __launch_bounds__(256) void prefill_attention_kernel(const FaParams p
   const uint16_t* kbase = p.k + (int64_t)tok0 * p.kv_stride + (int64_t)kv_head * D;
   const uint16_t* vbase = p.v + (int64_t)tok0 * p.kv_stride + (int64_t)kv_head * D;
   const int last_q = min(qt0 + QT, L) - 1;         // causal: keys 0 .. last_q
-  const int n_kt = last_q / FA_KT + 1;
+  const int n_kt = last_q / KT + 1;
   // sliding window: the tiles wholly before the window of the workgroup's first query are skipped
-  const int kt_lo = p.window > 0 ? max(qt0 - p.window + 1, 0) / FA_KT : 0;
+  const int kt_lo = p.window > 0 ? max(qt0 - p.window + 1, 0) / KT : 0;
   const float sc = p.scale;
   const float slope = p.alibi_slopes ? p.alibi_slopes[head] : 0.f;
   const bool every_tile = p.window > 0 || slope != 0.f;   // uniform: masks / bias touch every tile
@@ -102,10 +127,11 @@ __global__ __launch_bounds__(256) void prefill_attention_kernel(const FaParams p
   // tile loader: thread t owns pieces t, t+256, ... of the K and of the V tile (row = piece / (D/8))
   uint4 kreg[PPT], vreg[PPT];
   auto fetch = [&](int kt) {
-    const int k0 = kt * FA_KT;
+    const int k0 = kt * KT;
 #pragma unroll
     for (int i = 0; i < PPT; ++i) {
       const int id = threadIdx.x + i * 256;
+      if (RAGGED && i == PPT - 1 && id >= PIECES) break;
       const int row = id / (D / 8), c8 = id % (D / 8);
       const int64_t off = (int64_t)min(k0 + row, L - 1) * p.kv_stride + c8 * 8;   // rows past L: clamped,
       kreg[i] = ld16(kbase + off);                                                // masked through P = 0
@@ -116,25 +142,26 @@ __global__ __launch_bounds__(256) void prefill_attention_kernel(const FaParams p
 #pragma unroll
     for (int i = 0; i < PPT; ++i) {
       const int id = threadIdx.x + i * 256;
+      if (RAGGED && i == PPT - 1 && id >= PIECES) break;
       const int row = id / (D / 8), c8 = id % (D / 8);
       *reinterpret_cast<uint4*>(&kv_s[(buf * 2 + 0) * TILE + row * VS + c8 * 8]) = kreg[i];
       *reinterpret_cast<uint4*>(&kv_s[(buf * 2 + 1) * TILE + row * VS + c8 * 8]) = vreg[i];
     }
   };
   fetch(kt_lo);
-  park(kt_lo & 1);
+  park(DB ? kt_lo & 1 : 0);
   __syncthreads();
 
   for (int kt = kt_lo; kt < n_kt; ++kt) {
-    const int k0 = kt * FA_KT;
-    const int buf = kt & 1;
+    const int k0 = kt * KT;
+    const int buf = DB ? kt & 1 : 0;
     const uint16_t* k_s = &kv_s[(buf * 2 + 0) * TILE];
     const uint16_t* v_s = &kv_s[(buf * 2 + 1) * TILE];
     if (kt + 1 < n_kt) fetch(kt + 1);   // uniform; lands in registers while this tile is consumed
-    // ---- S^T = K . Q^T for the 4 key tiles: K rows from LDS (shared by the 4 waves) ----
-    f32x4_t s[QU][4];
+    // ---- S^T = K . Q^T for the NT key tiles: K rows from LDS (shared by the 4 waves) ----
+    f32x4_t s[QU][NT];
 #pragma unroll
-    for (int t = 0; t < 4; ++t) {
+    for (int t = 0; t < NT; ++t) {
 #pragma unroll
       for (int u = 0; u < QU; ++u) s[u][t] = f32x4_t{0.f, 0.f, 0.f, 0.f};
       const uint16_t* kp = k_s + (t * 16 + r) * VS + g * 8;
@@ -144,15 +171,22 @@ __global__ __launch_bounds__(256) void prefill_attention_kernel(const FaParams p
 #pragma unroll
         for (int u = 0; u < QU; ++u) s[u][t] = FaMfma<T>::run(kf, qf[u][c], s[u][t]);
       }
+      if constexpr (TAIL) {   // dims D - 16 + 4 g .. + 3 of key r against the same dims of the query
+        const uint2 kf = *reinterpret_cast<const uint2*>(kp - g * 4 + DC * 32);
+        // into an accumulator of its own, added by the VALU: chaining a 16x16x16 onto the result of a 16x16x32
+        // (another opcode reading it as srcC straight away) gave wrong logits on the hardware
+#pragma unroll
+        for (int u = 0; u < QU; ++u) s[u][t] += FaMfma<T>::run16(kf, qtail[u], f32x4_t{0.f, 0.f, 0.f, 0.f});
+      }
     }
     // ---- scale, causal / length mask, online softmax (row = this lane's query) ----
-    const bool diag = every_tile || k0 + FA_KT - 1 > qt0;   // uniform: else only tiles that reach past the first query
-    uint32_t pp[QU][8];                              // packed P: [t][pair]
+    const bool diag = every_tile || k0 + KT - 1 > qt0;   // uniform: else only tiles that reach past the first query
+    uint32_t pp[QU][2 * NT];                         // packed P: [t][pair]
 #pragma unroll
     for (int u = 0; u < QU; ++u) {
       float mx = -INFINITY;
 #pragma unroll
-      for (int t = 0; t < 4; ++t)
+      for (int t = 0; t < NT; ++t)
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const int key = k0 + t * 16 + 4 * g + i;
@@ -167,7 +201,7 @@ __global__ __launch_bounds__(256) void prefill_attention_kernel(const FaParams p
       const float alpha = __expf(m_run[u] - m_new);
       float psum = 0.f;
 #pragma unroll
-      for (int t = 0; t < 4; ++t) {
+      for (int t = 0; t < NT; ++t) {
         float e[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -183,9 +217,9 @@ __global__ __launch_bounds__(256) void prefill_attention_kernel(const FaParams p
 #pragma unroll
       for (int t = 0; t < DT; ++t) o[u][t] *= alpha;
     }
-    // ---- O^T += V^T . P^T : two 32-key steps, DT output tiles ----
+    // ---- O^T += V^T . P^T : NS 32-key steps, DT output tiles ----
 #pragma unroll
-    for (int st = 0; st < 2; ++st) {
+    for (int st = 0; st < NS; ++st) {
 #pragma unroll
       for (int t = 0; t < DT; ++t) {
         // A operand: V^T row d = 16 t + r, keys 32 st + {4g..4g+3, 16+4g..16+4g+3}: two hardware
@@ -201,8 +235,14 @@ __global__ __launch_bounds__(256) void prefill_attention_kernel(const FaParams p
           o[u][t] = FaMfma<T>::run(vf, make_uint4(pp[u][4 * st], pp[u][4 * st + 1], pp[u][4 * st + 2], pp[u][4 * st + 3]), o[u][t]);
       }
     }
-    if (kt + 1 < n_kt) park(buf ^ 1);   // the other buffer's readers finished before the last barrier
-    __syncthreads();
+    if constexpr (DB) {
+      if (kt + 1 < n_kt) park(buf ^ 1);   // the other buffer's readers finished before the last barrier
+      __syncthreads();
+    } else if (kt + 1 < n_kt) {           // uniform
+      __syncthreads();                    // every wave has read tile kt
+      park(0);
+      __syncthreads();                    // tile kt + 1 is visible
+    }
   }
   // ---- normalise and store: lane (q = r, g) holds d = 16 t + 4 g + i of its rows ----
 #pragma unroll
@@ -232,23 +272,8 @@ __global__ __launch_bounds__(256) void prefill_attention_kernel(const FaParams p
 // every key -- context and new -- is read from the cache: K [NB, KVH, D/8, BS, 8] gives the 16-byte
 // MFMA operand of a key directly (8 head dims), V [NB, KVH, D, BS] gives the V^T operand of a head
 // dim as two 8-byte runs of 4 consecutive tokens; no LDS at all.  Same transposed formulation as
-// the kernel above.
-struct PfxParams {
-  const uint16_t* q;    // [new tokens, H, D]
-  uint16_t* out;
-  const uint16_t* kc;   // key cache
-  const uint16_t* vc;   // value cache
-  const int* block_tables;   // [num_seqs, max_blocks]
-  const int* q_start;        // [num_seqs + 1] offsets of the new tokens
-  const int* seq_lens;       // [num_seqs] context + new
-  const int* ctx_lens;       // [num_seqs]
-  int64_t q_stride, o_stride, kv_block_stride, kv_head_stride;  // elements
-  int max_blocks, block_size, num_heads, num_kv_heads;
-  float scale;
-  const float* alibi_slopes;  // [H] or null
-  int window;                 // sliding window, 0 = none
-};
-
+// the kernel above.  Head sizes 64 and 128; 96, 112, 192 and 256 take prefix_attention_staged_kernel
+// (prefix_attention_staged.hip), which gathers a tile once per workgroup into LDS.  PfxParams: fa_common.h.
 template <typename T, int D>
 __global__ __launch_bounds__(256) void prefix_attention_kernel(const PfxParams p) {
   constexpr int DC = D / 32, DT = D / 16;
@@ -371,7 +396,12 @@ __global__ __launch_bounds__(256) void prefix_attention_kernel(const PfxParams p
 
 using namespace nmv;
 
-extern "C" int nmv_prefill_attention_supported(int head_size) { return head_size == 64 || head_size == 128; }
+// The kernels are written for any head size that is a multiple of 16; these are the ones instantiated.  80 is
+// not among them (the backend serves it with torch SDPA).
+extern "C" int nmv_prefill_attention_supported(int head_size) {
+  return head_size == 64 || head_size == 96 || head_size == 112 || head_size == 128 || head_size == 192 ||
+         head_size == 256;
+}
 
 extern "C" int nmv_prefill_attention(void* out, const void* q, const void* k, const void* v,
                                      const int32_t* cu_seqlens, int num_seqs, int max_seq_len,
@@ -380,7 +410,8 @@ extern "C" int nmv_prefill_attention(void* out, const void* q, const void* k, co
                                      const float* alibi_slopes, int sliding_window,
                                      nmv_dtype_t dtype, void* stream) {
   NMV_CHECK(dtype == NMV_F16 || dtype == NMV_BF16, "prefill_attention: fp16 / bf16 only");
-  NMV_CHECK(head_size == 64 || head_size == 128, "prefill_attention: head size %d not built (64, 128)", head_size);
+  NMV_CHECK(nmv_prefill_attention_supported(head_size),
+            "prefill_attention: head size %d not built (64, 96, 112, 128, 192, 256)", head_size);
   NMV_CHECK(num_kv_heads > 0 && num_heads % num_kv_heads == 0, "prefill_attention: heads %% kv_heads != 0");
   NMV_CHECK(q_stride % 8 == 0 && kv_stride % 8 == 0 && o_stride % 4 == 0,
             "prefill_attention: token strides must keep 16-byte (q, k, v) / 8-byte (out) alignment");
@@ -394,11 +425,17 @@ extern "C" int nmv_prefill_attention(void* out, const void* q, const void* k, co
   const int qu = 1;
   dim3 grid((max_seq_len + FA_QT * qu - 1) / (FA_QT * qu), num_heads, num_seqs), block(256);
 #define NMV_FA_LAUNCH(T_, D_) hipLaunchKernelGGL((prefill_attention_kernel<T_, D_, 1>), grid, block, 0, s, p);
-  if (dtype == NMV_BF16) {
-    if (head_size == 64) NMV_FA_LAUNCH(BF16, 64) else NMV_FA_LAUNCH(BF16, 128)
-  } else {
-    if (head_size == 64) NMV_FA_LAUNCH(F16, 64) else NMV_FA_LAUNCH(F16, 128)
+#define NMV_FA_HEADS(T_)                                  \
+  switch (head_size) {                                    \
+    case 64: NMV_FA_LAUNCH(T_, 64) break;                 \
+    case 96: NMV_FA_LAUNCH(T_, 96) break;                 \
+    case 112: NMV_FA_LAUNCH(T_, 112) break;               \
+    case 128: NMV_FA_LAUNCH(T_, 128) break;               \
+    case 192: NMV_FA_LAUNCH(T_, 192) break;               \
+    default: NMV_FA_LAUNCH(T_, 256) break;                \
   }
+  if (dtype == NMV_BF16) NMV_FA_HEADS(BF16) else NMV_FA_HEADS(F16)
+#undef NMV_FA_HEADS
 #undef NMV_FA_LAUNCH
   NMV_LAUNCH_CHECK();
   return NMV_OK;
@@ -414,7 +451,8 @@ extern "C" int nmv_prefix_prefill_attention(void* out, const void* q, const void
                                             int64_t kv_head_stride, const float* alibi_slopes,
                                             int sliding_window, nmv_dtype_t dtype, void* stream) {
   NMV_CHECK(dtype == NMV_F16 || dtype == NMV_BF16, "prefix_prefill_attention: fp16 / bf16 only (kv cache dtype auto)");
-  NMV_CHECK(head_size == 64 || head_size == 128, "prefix_prefill_attention: head size %d not built (64, 128)", head_size);
+  NMV_CHECK(nmv_prefill_attention_supported(head_size),
+            "prefix_prefill_attention: head size %d not built (64, 96, 112, 128, 192, 256)", head_size);
   NMV_CHECK(block_size == 8 || block_size == 16 || block_size == 32, "prefix_prefill_attention: block size %d", block_size);
   NMV_CHECK(num_kv_heads > 0 && num_heads % num_kv_heads == 0, "prefix_prefill_attention: heads %% kv_heads != 0");
   NMV_CHECK(q_stride % 8 == 0 && o_stride % 4 == 0, "prefix_prefill_attention: token strides break alignment");
@@ -425,7 +463,12 @@ extern "C" int nmv_prefix_prefill_attention(void* out, const void* q, const void
               sliding_window > 0 ? sliding_window : 0};
   dim3 grid((max_query_len + FA_QT - 1) / FA_QT, num_heads, num_seqs), block(256);
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == NMV_BF16) {
+  if (head_size != 64 && head_size != 128) {
+    NMV_CHECK(kv_block_stride % 8 == 0 && kv_head_stride % 8 == 0 && (uintptr_t)key_cache % 16 == 0 &&
+              (uintptr_t)value_cache % 16 == 0, "prefix_prefill_attention: cache planes must keep 16-byte alignment");
+    NMV_CHECK(launch_prefix_staged(p, dtype == NMV_BF16, head_size, grid, s),
+              "prefix_prefill_attention: no staged kernel for head size %d, block size %d", head_size, block_size);
+  } else if (dtype == NMV_BF16) {
     if (head_size == 64) hipLaunchKernelGGL((prefix_attention_kernel<BF16, 64>), grid, block, 0, s, p);
     else hipLaunchKernelGGL((prefix_attention_kernel<BF16, 128>), grid, block, 0, s, p);
   } else {
