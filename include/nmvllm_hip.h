@@ -415,6 +415,26 @@ int nmv_prefill_attention(void* out, const void* q, const void* k, const void* v
                           int num_kv_heads, int head_size, float scale, int64_t q_stride,
                           int64_t kv_stride, int64_t o_stride, const float* alibi_slopes,
                           int sliding_window, nmv_dtype_t dtype, void* stream);
+/* Block-sparse prompt attention (csrc/prefill_attention_blocksparse.hip): nmv_prefill_attention's tensors under the
+ * local + strided block pattern of the paged_attention block-sparse arguments.  With sb = blocksparse_block_size,
+ * qb = i / sb, kb = j / sb, query i of head h attends key j iff j <= i and
+ *   qb - kb < blocksparse_local_blocks   or   (kb + off_h) % blocksparse_vert_stride == 0,
+ *   off_h = (tp_rank * num_heads + h) * step + 1                 for step = blocksparse_head_sliding_step >= 0,
+ *   off_h = (tp_rank * num_kv_heads + kv_head(h)) * (-step) + 1  for step < 0
+ * -- the rule of paged_attention's decode kernel, so a sequence's prompt and decode steps see the same blocks (for
+ * step >= 0 also the reference's prompt mask, vllm/attention/ops/blocksparse_attention/utils.py:189-199; for step < 0
+ * the reference's prompt side ignores the head group, its decode kernel and this function do not).  Key tiles that
+ * hold no attended block are skipped, not masked.  blocksparse_vert_stride <= 1 forwards to nmv_prefill_attention.
+ * Otherwise refused: blocksparse_local_blocks < 1, a block size other than 16 / 32 / 64 / 128, fp32, a head size
+ * nmv_prefill_attention_supported() does not report.  No ALiBi, no sliding window (the reference's block-sparse
+ * backend asserts both away). */
+int nmv_prefill_attention_blocksparse(void* out, const void* q, const void* k, const void* v,
+                                      const int32_t* cu_seqlens, int num_seqs, int max_seq_len,
+                                      int num_heads, int num_kv_heads, int head_size, float scale,
+                                      int64_t q_stride, int64_t kv_stride, int64_t o_stride, int tp_rank,
+                                      int blocksparse_local_blocks, int blocksparse_vert_stride,
+                                      int blocksparse_block_size, int blocksparse_head_sliding_step,
+                                      nmv_dtype_t dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * W8A8: activation quantisers and the scaled matmul

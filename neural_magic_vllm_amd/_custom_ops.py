@@ -310,9 +310,14 @@ def get_max_shared_memory_per_block_device_attribute(device: int) -> int:
 # from Python, rocm_flash_attn.py:349-430); exposed here for the attention backend
 def prefill_attention(out: torch.Tensor, query: torch.Tensor, key: torch.Tensor, value: torch.Tensor,
                       cu_seqlens: torch.Tensor, max_seq_len: int, scale: float,
-                      alibi_slopes: Optional[torch.Tensor] = None, sliding_window: Optional[int] = None) -> None:
+                      alibi_slopes: Optional[torch.Tensor] = None, sliding_window: Optional[int] = None,
+                      tp_rank: int = 0, blocksparse_local_blocks: int = 0, blocksparse_vert_stride: int = 0,
+                      blocksparse_block_size: int = 64, blocksparse_head_sliding_step: int = 0) -> None:
+    """blocksparse_vert_stride > 1 selects the block-sparse prompt kernel (the five ints of paged_attention_v1)"""
     from neural_magic_vllm_amd import _torch_bindings as tb
-    tb.prefill_attention(out, query, key, value, cu_seqlens, max_seq_len, scale, alibi_slopes, sliding_window)
+    tb.prefill_attention(out, query, key, value, cu_seqlens, max_seq_len, scale, alibi_slopes, sliding_window,
+                         tp_rank, blocksparse_local_blocks, blocksparse_vert_stride, blocksparse_block_size,
+                         blocksparse_head_sliding_step)
 
 
 def prefill_attention_supported(head_size: int) -> bool:

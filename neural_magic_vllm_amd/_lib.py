@@ -28,7 +28,7 @@ class NmvError(RuntimeError):
 
 
 _lib: Optional[ctypes.CDLL] = None
-ABI_VERSION = 9  # nmv_abi_version() of the library this table describes (csrc/capi_common.hip)
+ABI_VERSION = 10  # nmv_abi_version() of the library this table describes (csrc/capi_common.hip)
 
 _P = c_void_p
 _I = c_int
@@ -126,6 +126,8 @@ SIGNATURES = {
     "nmv_prefix_prefill_attention_fp8": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _F,
                                               _L, _L, _L, _L, _P, _I, _I, _I, _F, _P]),
     "nmv_prefill_attention": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _L, _L, _L, _P, _I, _I, _P]),
+    "nmv_prefill_attention_blocksparse": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _L, _L, _L, _I, _I, _I, _I,
+                                               _I, _I, _P]),
     "nmv_gptq_shuffle": (_I, [_P, _P, _P, _I, _I, _I, _P]),
     "nmv_awq_gemm": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _L, _P]),
     "nmv_awq_dequantize": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),

@@ -440,11 +440,15 @@ def _alibi_arg(alibi_slopes, num_heads, like):
 
 
 def prefill_attention(out, query, key, value, cu_seqlens, max_seq_len, scale, alibi_slopes=None,
-                      sliding_window=None) -> None:
+                      sliding_window=None, tp_rank=0, blocksparse_local_blocks=0, blocksparse_vert_stride=0,
+                      blocksparse_block_size=64, blocksparse_head_sliding_step=0) -> None:
     """varlen causal GQA prompt attention (csrc/prefill_attention.hip); q [T, H, D], k/v [T, KVH, D]
     (last dim contiguous, may be slices of qkv), cu_seqlens int32 [num_seqs + 1]; optional ALiBi slopes
     (float32 [H]) and sliding window (keys fewer than that many positions back).  Head sizes 64, 96, 112, 128, 192
-    and 256 (prefill_attention_supported); anything else raises NmvError"""
+    and 256 (prefill_attention_supported); anything else raises NmvError.
+    blocksparse_vert_stride > 1: the local + strided block pattern of paged_attention_v1's block-sparse arguments
+    (csrc/prefill_attention_blocksparse.hip), which skips the key tiles no block of the pattern touches; then no
+    ALiBi and no sliding window, local blocks >= 1, block size 16 / 32 / 64 / 128"""
     _req(query.dim() == 3 and key.dim() == 3 and value.dim() == 3 and out.dim() == 3, "prefill_attention: [T, H, D] tensors")
     _req(query.stride(2) == 1 and key.stride(2) == 1 and value.stride(2) == 1 and out.stride(2) == 1,
          "prefill_attention: head dim must be contiguous")
@@ -454,6 +458,16 @@ def prefill_attention(out, query, key, value, cu_seqlens, max_seq_len, scale, al
          "prefill_attention: heads must be packed")
     _req(key.stride(0) == value.stride(0), "prefill_attention: k and v must share the token stride")
     _req(cu_seqlens.dtype == torch.int32 and cu_seqlens.is_contiguous(), "cu_seqlens must be int32")
+    if blocksparse_vert_stride > 1:
+        _req(alibi_slopes is None and not sliding_window,
+             "prefill_attention: block-sparse attention takes neither ALiBi slopes nor a sliding window")
+        with device_guard(query):
+            check(_lib.load().nmv_prefill_attention_blocksparse(
+                ptr(out), ptr(query), ptr(key), ptr(value), ptr(cu_seqlens), cu_seqlens.numel() - 1, int(max_seq_len),
+                h, kvh, d, float(scale), query.stride(0), key.stride(0), out.stride(0), int(tp_rank),
+                int(blocksparse_local_blocks), int(blocksparse_vert_stride), int(blocksparse_block_size),
+                int(blocksparse_head_sliding_step), dtype_code(query.dtype), stream_of(query)))
+        return
     with device_guard(query):
         check(_lib.load().nmv_prefill_attention(ptr(out), ptr(query), ptr(key), ptr(value), ptr(cu_seqlens),
                                                 cu_seqlens.numel() - 1, int(max_seq_len), h, kvh, d,

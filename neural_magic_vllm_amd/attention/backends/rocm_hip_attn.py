@@ -11,12 +11,13 @@ Prefix-enabled prefill (chunked prefill / prefix caching, PagedAttention.forward
 kv_cache_dtype "fp8" as well as "auto": the chunk then attends to the quantised values of its own
 tokens, which the cache write above has just stored (csrc/prefix_attention_fp8.hip).
 """
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 from typing import Any, Dict, List, Optional, Tuple, Type
 
 import torch
 
 from ... import _custom_ops as ops
+from ...distributed.parallel_state import get_tensor_model_parallel_rank, get_tensor_model_parallel_world_size
 from ..ops.paged_attn import PagedAttention, PagedAttentionMetadata
 from .abstract import AttentionBackend, AttentionImpl, AttentionMetadata
 
@@ -102,6 +103,37 @@ class ROCmHipAttentionMetadata(AttentionMetadata, PagedAttentionMetadata):
         return self._cached_decode_metadata
 
 
+@dataclass
+class BlocksparseParams:
+    """The reference's BlocksparseParams (blocksparse_attn.py:17-83): a head attends to the last `local_blocks` blocks
+    of `block_size` tokens and to every block with (block + head offset) % vert_stride == 0.  num_heads / num_kv_heads
+    are per tensor-parallel rank.  homo_head: one offset for all heads; homo_head_group: one per GQA group."""
+    max_seqlen: int
+    num_heads: int
+    num_kv_heads: int
+    block_size: int
+    local_blocks: int
+    vert_stride: int
+    homo_head: bool = False
+    homo_head_group: bool = False
+    head_sliding_step: int = field(init=False)       # negative: sliding along the kv heads
+    active_head_range: Tuple[int, int] = field(init=False)
+
+    def __post_init__(self):
+        assert self.block_size > 0
+        assert self.local_blocks >= 0
+        assert self.vert_stride >= 1
+        assert self.num_heads % self.num_kv_heads == 0
+        tp_size, tp_rank = get_tensor_model_parallel_world_size(), get_tensor_model_parallel_rank()
+        if self.homo_head:
+            self.head_sliding_step = 0
+        elif self.homo_head_group:
+            self.head_sliding_step = -max(1, int(self.vert_stride / (tp_size * self.num_kv_heads)))
+        else:
+            self.head_sliding_step = max(1, int(self.vert_stride / (tp_size * self.num_heads)))
+        self.active_head_range = (tp_rank * self.num_heads, (tp_rank + 1) * self.num_heads)
+
+
 class ROCmHipAttentionImpl(AttentionImpl):
     """Layout: |<-- prefill tokens -->|<-- decode tokens -->| in one flattened batch."""
 
@@ -109,9 +141,19 @@ class ROCmHipAttentionImpl(AttentionImpl):
                  num_kv_heads: Optional[int] = None, alibi_slopes: Optional[List[float]] = None,
                  sliding_window: Optional[int] = None, kv_cache_dtype: str = "auto",
                  blocksparse_params: Optional[Dict[str, Any]] = None) -> None:
-        # the decode op takes the block-sparse arguments (PagedAttention.forward_decode); the block-sparse PROMPT path
-        # is the reference's separate BlocksparseFlashAttentionBackend, which this backend does not replace
-        assert blocksparse_params is None, "block-sparse models need the reference's blocksparse backend for prompts"
+        # block-sparse layers (the reference's separate BlocksparseFlashAttentionBackend, blocksparse_attn.py:262-321):
+        # prompts run csrc/prefill_attention_blocksparse.hip, decode passes the same five ints to the paged-attention
+        # op, so both sides of a sequence see one mask
+        self.blocksparse_params: Optional[BlocksparseParams] = None
+        self.tp_rank = 0
+        if blocksparse_params is not None:
+            assert alibi_slopes is None, "ALiBi is not supported for block-sparse attention"
+            assert sliding_window is None, "sliding_window is invalid for block-sparse attention"
+            bp = dict(blocksparse_params)
+            bp.setdefault("num_heads", num_heads)
+            bp.setdefault("num_kv_heads", num_kv_heads or num_heads)
+            self.blocksparse_params = BlocksparseParams(**bp)
+            self.tp_rank = get_tensor_model_parallel_rank()
         # prompt attention masks the window in the kernel (rocm_flash_attn.py:244-246,394-406 hands it to
         # flash-attention / forward_prefix); decode sees it through the block tables and sequence lengths the
         # model runner builds, as in the reference (paged_attention takes no window)
@@ -157,6 +199,8 @@ class ROCmHipAttentionImpl(AttentionImpl):
         row [T, N] in the model dtype: rope + cache write + paged attention in ONE launch (PagedAttention.forward_decode_rope_partial).  Returns [T, hidden] or
         None when the fused form does not apply (then rope_and_cache_partial + forward)."""
         dm = attn_metadata.decode_metadata
+        if self.blocksparse_params is not None:   # the fused launch has no block-sparse form
+            return None
         if kv_cache is None or dm is None or attn_metadata.prefill_metadata is not None \
                 or attn_metadata.num_prefill_tokens != 0 or self.alibi_slopes is not None \
                 or not rotary_emb.is_neox_style or rotary_emb.rotary_dim != self.head_size \
@@ -222,13 +266,21 @@ class ROCmHipAttentionImpl(AttentionImpl):
         num_decode_tokens = attn_metadata.num_decode_tokens
         assert key.shape[0] == num_prefill_tokens + num_decode_tokens
 
+        # block-sparse layers: the five ints of both kernels; decode sizes its partitions by the model's longest
+        # sequence, as the reference does (blocksparse_attn.py:388-407)
+        bs = {}
+        if (bp := self.blocksparse_params) is not None:
+            bs = dict(tp_rank=self.tp_rank, blocksparse_local_blocks=bp.local_blocks,
+                      blocksparse_vert_stride=bp.vert_stride, blocksparse_block_size=bp.block_size,
+                      blocksparse_head_sliding_step=bp.head_sliding_step)
+
         if attn_metadata.prefill_metadata is None and num_decode_tokens == num_tokens:
             # decode-only batch (the hot path): no scatter into a separate output buffer
             dm = attn_metadata.decode_metadata
             out = PagedAttention.forward_decode(query, key_cache, value_cache, dm.block_tables,
-                                                dm.seq_lens_tensor, dm.max_decode_seq_len,
+                                                dm.seq_lens_tensor, bp.max_seqlen if bp else dm.max_decode_seq_len,
                                                 self.kv_cache_dtype, self.num_kv_heads, self.scale,
-                                                self.alibi_slopes, kv_scale)
+                                                self.alibi_slopes, kv_scale, **bs)
             return out.view(num_tokens, hidden_size)
 
         output = torch.empty((num_tokens, self.num_heads, self.head_size), dtype=query.dtype,
@@ -239,6 +291,8 @@ class ROCmHipAttentionImpl(AttentionImpl):
             if pm.context_lens_tensor is not None and kv_cache is not None \
                     and pm.block_tables is not None and pm.block_tables.numel() > 0 \
                     and bool((pm.context_lens_tensor > 0).any()):
+                if bp is not None:
+                    raise NotImplementedError("block-sparse attention does not support prefix-enabled prompts")
                 # prefix-enabled prefill (chunked prefill / prefix caching): every key comes from
                 # the paged cache, which already holds the new tokens (written above) -- with an fp8 cache, their
                 # quantised values
@@ -256,8 +310,11 @@ class ROCmHipAttentionImpl(AttentionImpl):
                 ops.prefill_attention(output[:num_prefill_tokens], query[:num_prefill_tokens],
                                       key[:num_prefill_tokens], value[:num_prefill_tokens], cu,
                                       pm.max_prefill_seq_len or max(pm.seq_lens), self.scale, self.alibi_slopes,
-                                      self.sliding_window)
+                                      self.sliding_window, **bs)
             else:
+                if bp is not None:
+                    raise NotImplementedError("block-sparse prompts need a head size the prompt kernel is built for "
+                                              "(64, 96, 112, 128, 192, 256) and fp16 / bf16")
                 if self.sliding_window is not None:
                     raise NotImplementedError("sliding-window prompts need a head size the prompt kernel is built "
                                               "for (64, 96, 112, 128, 192, 256) and fp16 / bf16")
@@ -270,8 +327,8 @@ class ROCmHipAttentionImpl(AttentionImpl):
         if (dm := attn_metadata.decode_metadata) is not None:
             output[num_prefill_tokens:] = PagedAttention.forward_decode(
                 decode_query, key_cache, value_cache, dm.block_tables, dm.seq_lens_tensor,
-                dm.max_decode_seq_len, self.kv_cache_dtype, self.num_kv_heads, self.scale,
-                self.alibi_slopes, kv_scale)
+                bp.max_seqlen if bp else dm.max_decode_seq_len, self.kv_cache_dtype, self.num_kv_heads, self.scale,
+                self.alibi_slopes, kv_scale, **bs)
         return output.view(num_tokens, hidden_size)
 
 

@@ -12,8 +12,7 @@ def get_attn_backend(num_heads: int, head_size: int, num_kv_heads: int,
                      sliding_window: Optional[int], dtype: torch.dtype,
                      kv_cache_dtype: Optional[str], block_size: int,
                      is_blocksparse: bool = False) -> Type[AttentionBackend]:
-    if is_blocksparse:
-        raise NotImplementedError("block-sparse attention is outside the hot-path scope")
+    # block-sparse layers (is_blocksparse) take the same backend: ROCmHipAttentionImpl accepts blocksparse_params
     if kv_cache_dtype not in (None, "auto", "fp8", "fp8_e4m3"):
         raise ValueError(f"kv cache dtype {kv_cache_dtype} is not supported on gfx950 "
                          "(OCP e4m3 only)")

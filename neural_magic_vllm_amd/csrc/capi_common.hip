@@ -26,7 +26,8 @@ void append_error(const char* fmt, ...) {
 extern "C" const char* nmv_last_error(void) { return nmv::g_err; }
 // 2: nmv_gptq_marlin_gemm_partial_splits takes num_groups; round-2 signature changes of the attention / fp8-marlin entry points
 // 9: nmv_prefix_prefill_attention_fp8
-extern "C" int nmv_abi_version(void) { return 9; }
+// 10: nmv_prefill_attention_blocksparse
+extern "C" int nmv_abi_version(void) { return 10; }
 
 extern "C" int64_t nmv_get_device_attribute(int64_t attribute, int64_t device_id) {
   int device = (int)device_id, value = 0;

@@ -1,6 +1,6 @@
-// What the prompt-attention kernels share (prefill_attention.hip, prefix_attention_staged.hip,
-// prefix_attention_fp8.hip): the tile sizes, the MFMAs of the model dtype, the logit mask and the parameters of
-// the 16-bit prefix kernels.
+// What the prompt-attention kernels share (prefill_attention.hip, prefill_attention_blocksparse.hip,
+// prefix_attention_staged.hip, prefix_attention_fp8.hip): the tile sizes and the tile plan per head size, the MFMAs
+// of the model dtype, the logit mask and the parameters of the 16-bit prefix kernels.
 #pragma once
 #include "common.h"
 
@@ -9,8 +9,26 @@ namespace nmv {
 constexpr int FA_QT = 64;   // queries per workgroup
 constexpr int FA_KT = 64;   // keys per iteration (head sizes up to 128; the wider ones choose their own, see the kernels)
 
+typedef short v4s_t __attribute__((ext_vector_type(4)));
+typedef v4s_t __attribute__((address_space(3))) lds_v4s_t;
 typedef short s16x4_t __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x4_t __attribute__((ext_vector_type(4)));
+
+// The tile plan per head size.  A K + V image pair of KT keys is 2 * KT * (D + 8) * 2 bytes.  A gfx950 CU has
+// 160 KiB of LDS and the compiler accepts more than 64 KiB of it per workgroup (head size 128 has always used
+// 69632 B), so the plan is a choice, not a limit: keep two workgroups on a CU.
+//   D <= 128  64 keys per iteration, double buffered (D = 112: 61440 B, D = 128: 69632 B)
+//   D  = 192  32 keys, double buffered (51200 B; 64 keys would be 102400 B: one workgroup per CU)
+//   D  = 256  32 keys, ONE buffer (33792 B): the next tile still waits in registers while this one is consumed, and
+//             is parked between two barriers, as prefix_attention_fp8_kernel does.  Two buffers (67584 B) were
+//             measured against it: DESIGN.md 3.8
+template <int D> struct FaPlan {
+  static constexpr int KT = D <= 128 ? FA_KT : 32;                          // keys per iteration
+  static constexpr bool DB = D != 256;                                      // double buffered
+  // waves per SIMD asked of the register allocator: the highest that leaves no scratch and that the LDS image
+  // lets run; 64 and 128 keep the allocator's default
+  static constexpr int WAVES = D == 64 || D == 128 ? 1 : (D == 96 || D == 192 ? 3 : 2);
+};
 
 template <typename T> struct FaMfma;
 template <> struct FaMfma<BF16> {

@@ -24,9 +24,6 @@
 
 namespace nmv {
 
-typedef short v4s_t __attribute__((ext_vector_type(4)));
-typedef v4s_t __attribute__((address_space(3))) lds_v4s_t;
-
 struct FaParams {
   const uint16_t* q;   // [tokens, H, D], token stride q_stride (elements)
   const uint16_t* k;   // [tokens, KVH, D], token stride kv_stride
@@ -38,22 +35,6 @@ struct FaParams {
   float scale;
   const float* alibi_slopes;  // [H] or null: bias slope * (key - query) on the scaled logits
   int window;                 // sliding window (0 = none): a query sees the keys less than `window` positions back
-};
-
-// The tile plan per head size.  A K + V image pair of KT keys is 2 * KT * (D + 8) * 2 bytes.  A gfx950 CU has
-// 160 KiB of LDS and the compiler accepts more than 64 KiB of it per workgroup (head size 128 has always used
-// 69632 B), so the plan is a choice, not a limit: keep two workgroups on a CU.
-//   D <= 128  64 keys per iteration, double buffered (D = 112: 61440 B, D = 128: 69632 B)
-//   D  = 192  32 keys, double buffered (51200 B; 64 keys would be 102400 B: one workgroup per CU)
-//   D  = 256  32 keys, ONE buffer (33792 B): the next tile still waits in registers while this one is consumed, and
-//             is parked between two barriers, as prefix_attention_fp8_kernel does.  Two buffers (67584 B) were
-//             measured against it: DESIGN.md 3.8
-template <int D> struct FaPlan {
-  static constexpr int KT = D <= 128 ? FA_KT : 32;                          // keys per iteration
-  static constexpr bool DB = D != 256;                                      // double buffered
-  // waves per SIMD asked of the register allocator: the highest that leaves no scratch and that the LDS image
-  // lets run; 64 and 128 keep the allocator's default
-  static constexpr int WAVES = D == 64 || D == 128 ? 1 : (D == 96 || D == 192 ? 3 : 2);
 };
 
 // QU = 16-query sub-tiles per wave: 1 (64 queries per workgroup; short prompts, more workgroups) or
