@@ -395,11 +395,11 @@ int nmv_prefix_prefill_attention(void* out, const void* q, const void* key_cache
                                  int64_t o_stride, int64_t kv_block_stride, int64_t kv_head_stride,
                                  const float* alibi_slopes, int sliding_window, nmv_dtype_t dtype,
                                  void* stream);
-/* The same on an fp8 KV cache (csrc/prefix_attention_fp8.hip; not in the reference, whose forward_prefix takes no
+/* The same on an fp8 KV cache (csrc/prefix_attention_fp8.hip, prefix_attention_fp8_wide.hip; not in the reference, whose forward_prefix takes no
  * cache dtype): key_cache [NB, KVH, D/16, BS, 16] and value_cache [NB, KVH, D, BS] hold e4m3 bytes, so the two
  * cache strides are in bytes; kv_dtype must be NMV_KV_FP8_E4M3; a cached byte b stands for e4m3(b) * kv_scale, as
- * for paged_attention.  fp16 / bf16 queries, head size 64 / 128 only (the fp8 path has not followed the 16-bit one
- * to 96 / 112 / 192 / 256), block size 8 / 16 / 32.  Every key and value is
+ * for paged_attention.  fp16 / bf16 queries, head size 64 / 96 / 112 / 128 / 192 / 256 (as the 16-bit path; 80 is
+ * refused), block size 8 / 16 / 32.  Every key and value is
  * read from the cache, the new tokens' included: a chunk attends to the quantised values of its own tokens. */
 int nmv_prefix_prefill_attention_fp8(void* out, const void* q, const void* key_cache,
                                      const void* value_cache, const int32_t* block_tables,

@@ -484,7 +484,8 @@ def prefix_prefill_attention(out, query, key_cache, value_cache, block_tables, q
     [NB, KVH, D/x, BS, x], value_cache [NB, KVH, D, BS].  kv_cache_dtype "auto": 16-bit caches in the model
     dtype, x = 8, head sizes 64 / 128 (csrc/prefill_attention.hip) and 96 / 112 / 192 / 256
     (csrc/prefix_attention_staged.hip).  "fp8" / "fp8_e4m3": uint8 caches of e4m3 bytes, x = 16, a byte
-    standing for e4m3(b) * kv_scale, head sizes 64 / 128 (csrc/prefix_attention_fp8.hip).  Either way every key and value comes from
+    standing for e4m3(b) * kv_scale, head sizes 64 / 128 (csrc/prefix_attention_fp8.hip) and 96 / 112 / 192 / 256
+    (csrc/prefix_attention_fp8_wide.hip).  Either way every key and value comes from
     the cache, the new tokens' included (the backend has written them): with an fp8 cache a chunk attends to
     the quantised values of its own tokens, the values every later decode step sees."""
     _req(query.dim() == 3 and out.dim() == 3 and query.stride(2) == 1 and out.stride(2) == 1,

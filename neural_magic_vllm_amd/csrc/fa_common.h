@@ -1,6 +1,7 @@
 // What the prompt-attention kernels share (prefill_attention.hip, prefill_attention_blocksparse.hip,
-// prefix_attention_staged.hip, prefix_attention_fp8.hip): the tile sizes and the tile plan per head size, the MFMAs
-// of the model dtype, the logit mask and the parameters of the 16-bit prefix kernels.
+// prefix_attention_staged.hip, prefix_attention_fp8.hip, prefix_attention_fp8_wide.hip): the tile sizes and the tile
+// plan per head size, the MFMAs of the model dtype, the logit mask and the parameters of the prefix kernels, 16-bit
+// and fp8 cache.
 #pragma once
 #include "common.h"
 
@@ -80,5 +81,32 @@ struct PfxParams {
 
 // launches prefix_attention_staged_kernel; false when (head_size, p.block_size) has no instantiation
 bool launch_prefix_staged(const PfxParams& p, bool bf16, int head_size, dim3 grid, hipStream_t s);
+
+// prefix-enabled prefill on an fp8 (e4m3) cache: prefix_attention_fp8_kernel (prefix_attention_fp8.hip, head sizes
+// 64 / 128) and prefix_attention_fp8_wide_kernel (prefix_attention_fp8_wide.hip, head sizes 96 / 112 / 192 / 256)
+struct Pfx8Params {
+  const uint16_t* q;    // [new tokens, H, D]
+  uint16_t* out;
+  const uint8_t* kc;    // key cache   [NB, KVH, D/16, BS, 16] e4m3
+  const uint8_t* vc;    // value cache [NB, KVH, D, BS] e4m3
+  const int* block_tables;   // [num_seqs, max_blocks]
+  const int* q_start;        // [num_seqs + 1] offsets of the new tokens
+  const int* seq_lens;       // [num_seqs] context + new
+  const int* ctx_lens;       // [num_seqs]
+  int64_t q_stride, o_stride;                  // elements
+  int64_t kv_block_stride, kv_head_stride;     // cache elements = bytes
+  int max_blocks, num_heads, num_kv_heads;
+  float scale, kv_scale;
+  const float* alibi_slopes;  // [H] or null
+  int window;                 // sliding window, 0 = none
+};
+
+// the low n bytes of a dword (n <= 0: none, n >= 4: all)
+__device__ __forceinline__ uint32_t low_bytes(int n) {
+  return n >= 4 ? 0xffffffffu : (n <= 0 ? 0u : (1u << (8 * n)) - 1u);
+}
+
+// launches prefix_attention_fp8_wide_kernel; false when (head_size, block_size) has no instantiation
+bool launch_prefix_fp8_wide(const Pfx8Params& p, bool bf16, int head_size, int block_size, dim3 grid, hipStream_t s);
 
 }  // namespace nmv

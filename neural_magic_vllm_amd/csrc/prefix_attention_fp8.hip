@@ -38,28 +38,6 @@
 
 namespace nmv {
 
-struct Pfx8Params {
-  const uint16_t* q;    // [new tokens, H, D]
-  uint16_t* out;
-  const uint8_t* kc;    // key cache   [NB, KVH, D/16, BS, 16] e4m3
-  const uint8_t* vc;    // value cache [NB, KVH, D, BS] e4m3
-  const int* block_tables;   // [num_seqs, max_blocks]
-  const int* q_start;        // [num_seqs + 1] offsets of the new tokens
-  const int* seq_lens;       // [num_seqs] context + new
-  const int* ctx_lens;       // [num_seqs]
-  int64_t q_stride, o_stride;                  // elements
-  int64_t kv_block_stride, kv_head_stride;     // cache elements = bytes
-  int max_blocks, num_heads, num_kv_heads;
-  float scale, kv_scale;
-  const float* alibi_slopes;  // [H] or null
-  int window;                 // sliding window, 0 = none
-};
-
-// the low n bytes of a dword (n <= 0: none, n >= 4: all)
-__device__ __forceinline__ uint32_t low_bytes(int n) {
-  return n >= 4 ? 0xffffffffu : (n <= 0 ? 0u : (1u << (8 * n)) - 1u);
-}
-
 template <typename T, int D, int BS>
 __global__ __launch_bounds__(256, D == 128 ? 3 : 4) void prefix_attention_fp8_kernel(const Pfx8Params p) {
   static_assert(D == 64 || D == 128, "head size");
@@ -281,7 +259,8 @@ extern "C" int nmv_prefix_prefill_attention_fp8(void* out, const void* q, const 
                                                 float kv_scale, void* stream) {
   NMV_CHECK(kv_dtype == NMV_KV_FP8_E4M3, "prefix_prefill_attention_fp8: kv cache dtype must be fp8 e4m3");
   NMV_CHECK(dtype == NMV_F16 || dtype == NMV_BF16, "prefix_prefill_attention_fp8: fp16 / bf16 queries only");
-  NMV_CHECK(head_size == 64 || head_size == 128, "prefix_prefill_attention_fp8: head size %d not built (64, 128)", head_size);
+  NMV_CHECK(head_size == 64 || head_size == 96 || head_size == 112 || head_size == 128 || head_size == 192 ||
+            head_size == 256, "prefix_prefill_attention_fp8: head size %d not built (64, 96, 112, 128, 192, 256)", head_size);
   NMV_CHECK(block_size == 8 || block_size == 16 || block_size == 32, "prefix_prefill_attention_fp8: block size %d", block_size);
   NMV_CHECK(num_kv_heads > 0 && num_heads % num_kv_heads == 0, "prefix_prefill_attention_fp8: heads %% kv_heads != 0");
   NMV_CHECK(q_stride % 8 == 0 && o_stride % 4 == 0, "prefix_prefill_attention_fp8: token strides break alignment");
@@ -294,7 +273,10 @@ extern "C" int nmv_prefix_prefill_attention_fp8(void* out, const void* q, const 
                sliding_window > 0 ? sliding_window : 0};
   const dim3 grid((max_query_len + FA_QT - 1) / FA_QT, num_heads, num_seqs);
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == NMV_BF16) {
+  if (head_size != 64 && head_size != 128) {   // prefix_attention_fp8_wide.hip
+    NMV_CHECK(launch_prefix_fp8_wide(p, dtype == NMV_BF16, head_size, block_size, grid, s),
+              "prefix_prefill_attention_fp8: no kernel for head size %d, block size %d", head_size, block_size);
+  } else if (dtype == NMV_BF16) {
     if (head_size == 64) launch_pfx8<BF16, 64>(block_size, grid, s, p);
     else launch_pfx8<BF16, 128>(block_size, grid, s, p);
   } else {
